@@ -7,22 +7,33 @@ multiScaleLoss, backward, Adam step.  With N GPUs: one process per GPU, per-GPU 
 (weak scaling); the only collective is the gradient all-reduce (bucketed, overlapped with
 the backward: distill.GraphedStep).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Besides the headline (configs[2]) it carries sub-records:
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it builds the
+step, warms up, times the K steps, writes the step's outputs if --dump-outputs is given and
+prints the headline (configs[2]) with `ms_per_step` and the `step_roofline` derived from it.
+--dump-outputs DIR writes what the last timed step left its caller, as float32 .npy files:
+`loss.npy` (the value the step returns) and `params.npy` (the student's parameters after
+that step, in parameter order; a fixed, seeded sample where they exceed the size cap, with
+the sampled positions in `params_index.npy`).  The inputs and the initial weights are seeded,
+so two builds run with the same arguments can be compared file by file.
+
+With --full the line also carries everything else the benchmark measures, each in runs of
+its own after the timed region: `host_enqueue_ms`, the per-kernel `roofline`, and the
+sub-records
   kd_step         configs[3]'s per-GPU slice: the KD step (teacher fwd + student fwd/bwd +
                   biDirection_loss_ht + Adam) at B=4 per GPU, its own timed region, roofline
                   and CPU baseline (every N: at N=8 it is configs[3]'s B=32 over 8 GPUs);
   configs1        configs[1] microbench (N=1): FPS, ball_query, grouping_operation, gather;
-  roofline_knn    configs[4] (N=1): culled kNN K=32 at N=65536, B=4;
-  step_roofline   the whole step against the model's algorithmic flops / bytes.
-`roofline` objects are measured live: HIP events on the launch stream around the timed
-launches, algorithmic bytes (or flops) per launch from SURVEY §8d.  `traffic` is the PMC
+  roofline_knn    configs[4] (N=1): culled kNN K=32 at N=65536, B=4.
+`step_roofline` (every run) is the whole step against the model's algorithmic flops / bytes.
+`roofline` objects (--full) are measured live: HIP events on the launch stream around the
+timed launches, algorithmic bytes (or flops) per launch from SURVEY §8d.  `traffic` is the PMC
 HBM bytes per launch from profiles/pmc_traffic.json for the SAME (workload, entry) only,
 else null.  `cpu_baseline` is the oracle's pure-PyTorch CPU restatement of the reference
 path (square_distance+topk kNN, torch.gather indexing, FPS replaced by a random subsample)
-on a bounded sample, rank 0 at N=1 only.
+on a bounded sample, rank 0 at N=1 only (--full).
 """
 import argparse
 import json
@@ -112,9 +123,17 @@ def parse(argv=None):
     ap.add_argument("--npoints", type=int, default=8192)
     ap.add_argument("--mode", choices=["train", "kd"], default="train",
                     help="the headline step (kd: the KD step at --batch is the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: host enqueue "
+                         "time, per-kernel roofline, the --sections besides the headline and "
+                         "the CPU baselines (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss.npy, params.npy) "
+                         "into DIR")
     ap.add_argument("--sections", default="train,kd,configs1,knn",
                     help="comma list of train, kd, configs1, knn, gather_c3, gather_c64 "
-                         "(PMC passes run one each)")
+                         "(PMC passes run one each); sections other than the headline step "
+                         "need --full")
     ap.add_argument("--roofline-kernel", default=PRIMARY_KERNEL)
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -220,11 +239,71 @@ def cpu_baseline(args, mode):
                       f"host os.cpu_count()={os.cpu_count()}"}
 
 
-# --------------------------------------------------------------------------- step section
-def step_section(args, mode, batch, dev, world, rank):
-    """Build the (graphed) train or KD step at `batch` pairs per GPU, time args.steps of it,
-    then the live per-kernel roofline of args.roofline_kernel over eager replays."""
+# ------------------------------------------------- after the timed region (--full only)
+def _host_and_roofline(args, mode, batch, eager, batches):
+    """After the timed region (--full): the host enqueue time of one eager step in ms, and
+    the live roofline object of args.roofline_kernel."""
     import kdpc_native
+    nb = len(batches)
+    # host enqueue time of one eager step (Python / torch.ops issue time from an idle device)
+    host = []
+    for i in range(2):
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        eager(*batches[i % nb])
+        host.append(time.perf_counter() - h0)
+        torch.cuda.synchronize()
+
+    # per-kernel roofline: HIP events around every launch of the entry point, over eager
+    # replays of the same step after the timed region (a graph replay has no per-launch host
+    # hook); kernel durations do not depend on how the launch was issued
+    timer = kdpc_native.LaunchTimer([args.roofline_kernel], lead_cycles=250000)  # ~100 us
+    kdpc_native.set_launch_timer(timer)
+    # spin kernels bracket the window in a kernel trace (tools/roofline_check.py counts only
+    # the launches between them: the graph replays run the entry's kernels concurrently with
+    # the parameter-gradient stream, which lengthens them)
+    torch.cuda.synchronize()
+    torch.cuda._sleep(64)
+    torch.cuda.synchronize()
+    for i in range(args.measure_steps):
+        eager(*batches[i % nb])
+    torch.cuda.synchronize()
+    torch.cuda._sleep(64)
+    torch.cuda.synchronize()
+    kdpc_native.set_launch_timer(None)
+    s = timer.summary().get(args.roofline_kernel)
+    wl = workload_key(mode, batch, args.npoints)
+    roof = None if not s else roofline_obj(args.roofline_kernel, wl, s["ms"], s["launches"],
+                                           s["bytes"], s["flops"])
+    return round(min(host) * 1e3, 3), roof
+
+
+# ----------------------------------------------------------------------- dumped outputs
+DUMP_CAP_BYTES = 64 << 20  # all files of one --dump-outputs directory together
+
+
+def dump_outputs(path, arrays, cap=DUMP_CAP_BYTES):
+    """Write `arrays` (name -> tensor) as <path>/<name>.npy in float32.  An array over its
+    share of `cap` is cut to a fixed, seeded sample of its flattened elements, whose (sorted)
+    positions go to <name>_index.npy and count against the same share."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = cap // max(len(arrays), 1) - 2 * 128  # less the two files' .npy headers
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > share:
+            keep = share // (a.itemsize + 8)  # a float32 value and its int64 position
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.int64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+
+
+# --------------------------------------------------------------------------- step section
+def step_section(args, mode, batch, dev, world, rank, full=True, dump_dir=None):
+    """Build the (graphed) train or KD step at `batch` pairs per GPU and time args.steps of
+    it; write the last step's outputs to `dump_dir` if given; with `full`, then the host
+    enqueue time and the live per-kernel roofline of args.roofline_kernel over eager replays."""
     import synthetic
     from distill import (FlowTrainStep, KDTrainStep, graphed_flow_step, graphed_kd_step,
                          make_optimizer, wrap_ddp)
@@ -285,7 +364,7 @@ def step_section(args, mode, batch, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
-        step(*batches[i % nb], **nxt(i))
+        last = step(*batches[i % nb], **nxt(i))
     t_issue = time.perf_counter() - t0  # host time to issue the K steps (graph replays)
     torch.cuda.synchronize()
     if world > 1:
@@ -296,42 +375,22 @@ def step_section(args, mode, batch, dev, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # host enqueue time of one eager step (Python / torch.ops issue time from an idle device)
-    host = []
-    for i in range(2):
-        torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        eager(*batches[i % nb])
-        host.append(time.perf_counter() - h0)
-        torch.cuda.synchronize()
+    if dump_dir is not None and rank == 0:
+        # the step returns its loss and leaves the updated parameters in the model
+        with torch.no_grad():
+            dump_outputs(dump_dir, {
+                "loss": last.reshape(1),
+                "params": torch.cat([p.reshape(-1) for p in student.parameters()])})
 
-    # per-kernel roofline: HIP events around every launch of the entry point, over eager
-    # replays of the same step after the timed region (a graph replay has no per-launch host
-    # hook); kernel durations do not depend on how the launch was issued
-    timer = kdpc_native.LaunchTimer([args.roofline_kernel], lead_cycles=250000)  # ~100 us
-    kdpc_native.set_launch_timer(timer)
-    # spin kernels bracket the window in a kernel trace (tools/roofline_check.py counts only
-    # the launches between them: the graph replays run the entry's kernels concurrently with
-    # the parameter-gradient stream, which lengthens them)
-    torch.cuda.synchronize()
-    torch.cuda._sleep(64)
-    torch.cuda.synchronize()
-    for i in range(args.measure_steps):
-        eager(*batches[i % nb])
-    torch.cuda.synchronize()
-    torch.cuda._sleep(64)
-    torch.cuda.synchronize()
-    kdpc_native.set_launch_timer(None)
-    s = timer.summary().get(args.roofline_kernel)
-    wl = workload_key(mode, batch, args.npoints)
-    roof = None if not s else roofline_obj(args.roofline_kernel, wl, s["ms"], s["launches"],
-                                           s["bytes"], s["flops"])
+    host_ms, roof = None, None
+    if full:
+        host_ms, roof = _host_and_roofline(args, mode, batch, eager, batches)
     pairs = world * batch * args.steps
     ms = dt / args.steps * 1e3
     res = {"value": round(pairs / dt, 3), "unit": "pairs/s", "ms_per_step": round(ms, 3),
            "steps": args.steps, "warmup": args.warmup, "batch_per_gpu": batch,
            "global_batch": world * batch, "step": step_kind,
-           "host_enqueue_ms": round(min(host) * 1e3, 3),
+           "host_enqueue_ms": host_ms,
            "host_issue_ms_per_step": round(t_issue / args.steps * 1e3, 3),
            "roofline": roof,
            "step_roofline": {
@@ -566,10 +625,16 @@ def main(argv=None):
     sections = set(args.sections.split(","))
     head_mode = args.mode
     head_batch = args.batch
+    if not args.full:  # a plain run: the headline step's timed region and nothing else
+        if head_mode not in sections:
+            raise SystemExit(f"bench.py: --sections {args.sections} without the headline step "
+                             f"({head_mode}) needs --full")
+        sections = {head_mode}
     line = {}
     head = None
     if head_mode in sections:
-        head = step_section(args, head_mode, head_batch, dev, world, rank)
+        head = step_section(args, head_mode, head_batch, dev, world, rank, full=args.full,
+                            dump_dir=args.dump_outputs)
     sub_kd = None
     if head_mode == "train" and "kd" in sections:
         sub_kd = step_section(args, "kd", args.kd_batch, dev, world, rank)
@@ -596,10 +661,11 @@ def main(argv=None):
                        "batch_per_gpu": head_batch, "global_batch": world * head_batch,
                        "npoints": args.npoints, "parallelism": f"dp{world}",
                        "step": head["step"]},
-            "host_enqueue_ms": head["host_enqueue_ms"],
-            "roofline": head["roofline"],
             "step_roofline": head["step_roofline"],
         }
+        if args.full:
+            line["host_enqueue_ms"] = head["host_enqueue_ms"]
+            line["roofline"] = head["roofline"]
     if sub_kd is not None:
         sub_kd["workload"] = ("KD step: teacher fwd (eval, no_grad) + student fwd+bwd + "
                               "biDirection_loss_ht(gamma=0.3, beta=0.8, layer=3) + Adam "
@@ -612,7 +678,7 @@ def main(argv=None):
         line["roofline_gather"] = cfg1["grouping_operation_rotated"]
     if knn is not None:
         line["roofline_knn"] = knn
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if head is not None:
             line["cpu_baseline"] = cpu_baseline(args, head_mode)
         if sub_kd is not None:

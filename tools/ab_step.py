@@ -1,6 +1,6 @@
 """Whole-step A/B without touching the package: set module attributes, then run bench.py.
 
-    python tools/ab_step.py wgrad.enabled=0 wgrad._NSTREAMS=1 -- --sections train --steps 20
+    python tools/ab_step.py wgrad.enabled=0 wgrad._NSTREAMS=1 -- --full --sections train --steps 20
 
 Each `module.attr=value` (int / float / True / False) is set after importing the module from
 kd-pointcloud_amd; everything after `--` goes to bench.main().

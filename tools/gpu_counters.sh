@@ -12,7 +12,7 @@ KREGEX=${KREGEX:-pc_bwd|pc_fwd|cost_volume_|cvw_fused|cv_rows_sum}
 O="$R/gpurun_out/$OUT"
 mkdir -p "$O"
 timeout -s KILL 60 rocprofv3 -L > "$O/counters_list.txt" 2>&1 || true
-CMD="python3 $R/bench.py --sections $SECTION --steps 2 --warmup 1 --no-cpu-baseline --measure-steps 1"
+CMD="python3 $R/bench.py --full --sections $SECTION --steps 2 --warmup 1 --no-cpu-baseline --measure-steps 1"
 PASSES=(
   "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE GRBM_COUNT"
   "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_MFMA SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE"

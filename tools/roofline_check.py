@@ -5,7 +5,7 @@
 For each roofline object in the bench line (the headline `roofline`, `kd_step.roofline`,
 `configs1.*`, `roofline_knn`, ...): rocprof per-launch duration = the summed durations of its
 entry's HIP kernels / launches of its first kernel, next to the live HIP-event average
-(avg_launch_us).  Profile a single-section bench command (`--sections train`, `kd`,
+(avg_launch_us).  Profile a single-section bench command (`--full --sections train`, `kd`,
 `configs1` or `knn`): the rocprof sums cover every launch in the process, except for the
 train / KD entries, which count the launches inside the measurement window bench.py marks
 with two spin kernels (torch.cuda._sleep).

@@ -489,6 +489,24 @@ int kdpc_idw_blend_bwd_coords(int b, int n, int s, int c, const float *ref, cons
                               const float *vals, const int *idx, const float *dout,
                               float *drow, float *dqry, int warp, void *stream);
 
+/* ---- full-scan flow propagation (inference; no reference counterpart: the reference answers
+ *      only for the points it was fed) -------------------------------------------------- */
+
+/* The model's UpsampleFlow rule carried from the N anchors it saw to every point of a ragged
+ * batch of scans, in one kernel: for each query row of cloud i, the 3 nearest anchors of
+ * cloud i exactly as kdpc_three_nn selects them (direct-difference distances, strict <: the
+ * lower index wins ties, indices always in [0,N)), then exactly kdpc_idw_blend_fwd's blend
+ * with warp = 0 of vals over them.  anchors (B,N,3), vals (B,N,C), qry (m_total,3): every
+ * cloud's queries packed, cloud i = rows offsets[i] .. offsets[i+1] (offsets: B+1 int64 in
+ * device memory; each range is clamped to [0, m_total) by the kernel), out (m_total,C),
+ * idx_out (m_total,3) the selected anchors or NULL.  max_len: an upper bound of the cloud
+ * lengths (it sizes the grid; rows of a longer cloud past it are not written); a cloud may
+ * be empty.  Writes out / idx_out only: no workspace, no atomics, capture-safe.
+ * N >= 3, C >= 1, B <= 65535; B == 0 or m_total == 0 is a no-op. */
+int kdpc_flow_propagate(int b, int n, int c, long long m_total, int max_len,
+                        const float *anchors, const float *vals, const float *qry,
+                        const long long *offsets, float *out, int *idx_out, void *stream);
+
 /* ---- skinny 1x1-layer weight gradients (dense_small.hip) ---------------------------- */
 
 /* out (O x I) = A^T B for row-major A (R x O), B (R x I), min(O,I) <= 4, O + I <= 512: slab

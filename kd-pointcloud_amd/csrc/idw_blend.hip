@@ -15,6 +15,7 @@
 // Layout (point-major): ref (B,S,3), qry (B,N,3), vals (B,S,C), idx (B,N,3) int32 in [0,S),
 // out (B,N,C), w (B,N,3).  No float atomics: the scatter of the values / reference-point
 // gradients goes through the CSR of idx (ascending (n, k) position per reference point).
+#include "idw_math.h"  // Geo3, idw_geometry, idw_blend3 (shared with flow_propagate.hip)
 #include "kdpc_common.h"
 
 #include <algorithm>
@@ -22,42 +23,6 @@
 using namespace kdpc;
 
 namespace {
-
-constexpr float kMinDist = 1e-10f;  // .clamp(min=1e-10) of the reference
-
-struct Geo3 {
-  float g[3][3];  // g_k = ref[idx_k] - q
-  float len[3];   // ||g_k||
-  float r[3];     // 1 / max(||g_k||, 1e-10)
-  float w[3];     // r_k / sum r
-  float sum;      // r_0 + r_1 + r_2
-  int nb[3];      // global reference rows b*S + idx_k
-};
-
-__device__ __forceinline__ void idw_geometry(const float* __restrict__ ref,
-                                             const float* __restrict__ qry,
-                                             const int* __restrict__ idx, long long row, int s,
-                                             int bi, Geo3& o) {
-  const float qx = qry[row * 3 + 0], qy = qry[row * 3 + 1], qz = qry[row * 3 + 2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int nb = bi * s + idx[row * 3 + k];
-    o.nb[k] = nb;
-    const float gx = ref[(long long)nb * 3 + 0] - qx;
-    const float gy = ref[(long long)nb * 3 + 1] - qy;
-    const float gz = ref[(long long)nb * 3 + 2] - qz;
-    o.g[k][0] = gx;
-    o.g[k][1] = gy;
-    o.g[k][2] = gz;
-    const float len = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy)),
-                                           __fmul_rn(gz, gz)));
-    o.len[k] = len;
-    o.r[k] = __fdiv_rn(1.0f, fmaxf(len, kMinDist));
-  }
-  o.sum = __fadd_rn(__fadd_rn(o.r[0], o.r[1]), o.r[2]);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) o.w[k] = __fdiv_rn(o.r[k], o.sum);
-}
 
 // one thread per (query row, 4 channels)
 __global__ __launch_bounds__(256) void idw_fwd_kernel(int b, int n, int s, int c,
@@ -85,10 +50,7 @@ __global__ __launch_bounds__(256) void idw_fwd_kernel(int b, int n, int s, int c
 #pragma unroll
       for (int k = 0; k < 3; ++k)
         x[k] = *reinterpret_cast<const float4*>(vals + (long long)o.nb[k] * c + 4 * v);
-      auto blend = [&](float a0, float a1, float a2) {
-        return __fadd_rn(__fadd_rn(__fmul_rn(o.w[0], a0), __fmul_rn(o.w[1], a1)),
-                         __fmul_rn(o.w[2], a2));
-      };
+      auto blend = [&](float a0, float a1, float a2) { return idw_blend3(o, a0, a1, a2); };
       *reinterpret_cast<float4*>(out + row * c + 4 * v) =
           make_float4(blend(x[0].x, x[1].x, x[2].x), blend(x[0].y, x[1].y, x[2].y),
                       blend(x[0].z, x[1].z, x[2].z), blend(x[0].w, x[1].w, x[2].w));
@@ -98,9 +60,9 @@ __global__ __launch_bounds__(256) void idw_fwd_kernel(int b, int n, int s, int c
     for (int i = 0; i < 4; ++i) {
       const int ch = 4 * v + i;
       if (ch >= c) break;
-      float acc = __fmul_rn(o.w[0], vals[(long long)o.nb[0] * c + ch]);
-      acc = __fadd_rn(acc, __fmul_rn(o.w[1], vals[(long long)o.nb[1] * c + ch]));
-      acc = __fadd_rn(acc, __fmul_rn(o.w[2], vals[(long long)o.nb[2] * c + ch]));
+      const float acc = idw_blend3(o, vals[(long long)o.nb[0] * c + ch],
+                                   vals[(long long)o.nb[1] * c + ch],
+                                   vals[(long long)o.nb[2] * c + ch]);
       out[row * c + ch] = warp ? __fsub_rn(qry[row * 3 + ch], acc) : acc;
     }
   }
@@ -183,7 +145,7 @@ __global__ __launch_bounds__(256) void idw_bwd_coords_kernel(
       // d||g||/dg = g / ||g||
       const float dr = __fadd_rn(__fmul_rn(dw[k], inv), dnorm);
       const float dd = -__fmul_rn(dr, __fmul_rn(o.r[k], o.r[k]));
-      const bool pass = o.len[k] >= kMinDist;
+      const bool pass = o.len[k] >= kIdwMinDist;
       const float sc = pass ? __fdiv_rn(dd, o.len[k]) : 0.f;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {

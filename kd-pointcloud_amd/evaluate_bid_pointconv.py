@@ -9,7 +9,11 @@ batches arrive in HBM one step ahead (datasets.DeviceLoader), the forward runs u
 inference mode, and every metric -- multiScaleLoss, EPE3D, ACC3DS/R, outliers, EPE2D,
 ACC2D -- is computed on the device and accumulated there; the host reads the totals once,
 at the end, instead of the reference's five `.cpu()` copies and NumPy metrics per batch.
-Checkpoints load with torch.load(weights_only=True)."""
+Checkpoints load with torch.load(weights_only=True).
+
+`dense: true` in the configuration (with `dense_seed`, default 0) evaluates on ALL points of
+every scan instead (evaluate_dense): the model sees `num_points` sampled anchors per scan and
+its flow is propagated to every point (inference.FlowPredictor.predict_dense)."""
 import os
 import sys
 import types
@@ -63,6 +67,43 @@ def evaluate(model, loader, calib_dir=None, loss_fn=None):
     return res
 
 
+DENSE_METRICS = METRICS[2:]
+
+
+def evaluate_dense(model, loader, num_points, seed, calib_dir=None):
+    """The metrics on ALL points of every scan (config keys `dense: true`, `dense_seed`).
+    `loader` yields whole scans at batch size 1 (ProcessData with num_points <= 0 keeps every
+    point that passes the depth mask).  Each pair goes through
+    inference.FlowPredictor.predict_dense: the model sees `num_points` anchors drawn from each
+    scan (generator seeded with `seed`), replayed from one HIP graph, and its flow is carried
+    to every point by the 3-nearest-anchor inverse-distance blend.  EPE3D / ACC3DS / ACC3DR /
+    Outliers3D / EPE2D / ACC2D are per-scan values over all of the scan's points, averaged
+    over scans, accumulated on the device and read once."""
+    from inference import FlowPredictor
+    predictor = FlowPredictor(model, 1, num_points)
+    gen = torch.Generator().manual_seed(int(seed))
+    acc = None
+    nb = points = 0
+    for pos1, pos2, _, _, flow, paths in loader:
+        if pos1.shape[0] != 1:
+            raise ValueError("evaluate_dense: whole scans have different lengths; use batch "
+                             f"size 1 (got {pos1.shape[0]})")
+        dense = predictor.predict_dense([pos1[0]], [pos2[0]], gen)[0]
+        full = dense.unsqueeze(0)
+        m3 = evaluate_3d(full, flow)
+        fp, fg = geometry.get_batch_2d_flow(pos1, pos1 + flow, pos1 + full, paths, calib_dir)
+        m2 = evaluate_2d(fp, fg)
+        row = torch.stack([v.reshape(()).double() for v in (*m3, *m2)])
+        acc = row if acc is None else acc + row
+        nb += 1
+        points += pos1.shape[1]
+    if acc is None:
+        raise RuntimeError("evaluate_dense: empty loader")
+    res = {k: v / nb for k, v in zip(DENSE_METRICS, acc.cpu().tolist())}
+    res["batches"], res["samples"], res["points"] = nb, nb, points
+    return res
+
+
 def format_result(r):
     """The reference's report line (evaluate_bid_pointconv.py:150-166)."""
     return (" * EPE3D {:.4f}\tACC3DS {:.4f}\tACC3DR {:.4f}\tOutliers3D {:.4f}\tEPE2D {:.4f}\t"
@@ -104,6 +145,17 @@ def main(config_path):
         raise ValueError("no checkpoint: set `pretrain` (with `ckpt_dir`), or "
                          "`allow_random_init: true` to evaluate random-init weights")
     model.to(dev)
+    if getattr(args, "dense", False):
+        # whole scans (num_points <= 0 keeps every point), one pair per batch; the model
+        # sees args.num_points anchors of each
+        whole = types.SimpleNamespace(**dict(vars(args), num_points=0))
+        loader = datasets.DeviceLoader(make_val_dataset(whole), 1, dev,
+                                       num_workers=getattr(args, "workers", 0))
+        r = evaluate_dense(model, loader, args.num_points, getattr(args, "dense_seed", 0),
+                           calib_dir=getattr(args, "calib_dir", None))
+        print("Dense evaluation: %d scans, %d points" % (r["samples"], r["points"]))
+        print(format_result(r))
+        return r
     loader = datasets.DeviceLoader(make_val_dataset(args), args.batch_size, dev,
                                    num_workers=getattr(args, "workers", 0))
     r = evaluate(model, loader, calib_dir=getattr(args, "calib_dir", None))

@@ -6,7 +6,8 @@ Two layers over libkdpc_hip.so (the C ABI in include/kdpc.h):
     scratch from the caching allocator, launched on the current torch stream.  Every op
     function below goes through it;
   * a ctypes binding of the bare C ABI (load_library, _SIGNATURES), used by the C-ABI
-    tests (export / arity / argument validation) and by build-id verification.
+    tests (export / arity / argument validation), by build-id verification and by the two
+    ops that have no torch operator (knn_point_evals, flow_propagate).
 There is no CPU path: a missing library or a CPU tensor raises.
 """
 import ctypes
@@ -104,6 +105,7 @@ _SIGNATURES = {
     "kdpc_idw_blend_fwd": [_c_int] * 4 + [_vp] * 6 + [_c_int, _vp],
     "kdpc_idw_blend_bwd_vals": [_c_int] * 4 + [_vp] * 5 + [_c_int, _vp],
     "kdpc_idw_blend_bwd_coords": [_c_int] * 4 + [_vp] * 7 + [_c_int, _vp],
+    "kdpc_flow_propagate": [_c_int] * 3 + [_c_longlong, _c_int] + [_vp] * 7,
     "kdpc_dense_tn_small_workspace_bytes": [_c_int] * 3,
     "kdpc_dense_tn_small": [_c_int] * 3 + [_vp] * 4 + [_c_size, _vp],
     "kdpc_dense_small": [_c_int] * 3 + [_vp] * 5,
@@ -815,6 +817,33 @@ def idw_blend_bwd_coords(ref, qry, vals, idx, dout, warp=False):
     """-> (drow (B,3N,3) per-neighbour rows of d/d ref, dqry (B,N,3))."""
     return _op("kdpc_idw_blend_bwd_coords", "idw_blend_bwd_coords", _gpu(ref, "ref"), qry,
                vals, idx, dout.contiguous(), bool(warp))
+
+
+def flow_propagate(anchors, vals, qry, offsets, max_len, return_idx=False):
+    """Full-scan propagation (kdpc_flow_propagate, through the bare C ABI): anchors (B,N,3),
+    vals (B,N,C), qry (M_total,3) every cloud's queries packed, offsets (B+1) int64 on the
+    device (cloud i = rows offsets[i]..offsets[i+1]), max_len >= the longest cloud (a host
+    int: it sizes the grid) -> out (M_total,C) [, idx (M_total,3) i32]: three_nn's neighbours
+    and idw_blend_fwd's blend of vals over them, in one kernel.  See include/kdpc.h."""
+    lib = load_library()
+    B, N, _ = anchors.shape
+    C, M = vals.shape[2], qry.shape[0]
+    if anchors.shape != (B, N, 3) or vals.shape[:2] != (B, N) or qry.shape != (M, 3):
+        raise ValueError("flow_propagate: anchors (B,N,3), vals (B,N,C), qry (M,3) expected, got "
+                         f"{tuple(anchors.shape)}, {tuple(vals.shape)}, {tuple(qry.shape)}")
+    if offsets.shape != (B + 1,):
+        raise ValueError(f"flow_propagate: offsets must hold B+1 = {B + 1} values")
+    pa = _dev(anchors, torch.float32, "anchors")
+    pv = _dev(vals, torch.float32, "vals")
+    pq = _dev(qry, torch.float32, "qry")
+    po = _dev(offsets, torch.int64, "offsets")
+    out = torch.empty((M, C), dtype=torch.float32, device=anchors.device)
+    idx = (torch.empty((M, 3), dtype=torch.int32, device=anchors.device) if return_idx
+           else None)
+    _call("kdpc_flow_propagate", B, N, C, M, int(max_len), pa, pv, pq, po, out.data_ptr(),
+          idx.data_ptr() if return_idx else None, _stream(anchors),
+          work=(12.0 * M + 4.0 * C * M + (12 + 4 * C) * B * N, 8.0 * M * N))
+    return (out, idx) if return_idx else out
 
 
 # ------------------------------------------------------------------- fused WeightNet

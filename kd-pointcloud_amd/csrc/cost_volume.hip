@@ -19,7 +19,10 @@
 // sparse row update in LDS; dz0 = dh0 * LeakyReLU'(h0); then
 //   dP1[n] = sum_k dz0[k]              (written directly)
 //   dP2 rows, d(dir) rows              (per (n,k) rows; summed per reference point through the
-//                                       kNN index's CSR: deterministic, no float atomics)
+//                                       kNN index's CSR: deterministic, no float atomics.  In
+//                                       the CSR workspace a neighbour row no output routes to
+//                                       -- exactly +0 -- is not written nor read back: the .w
+//                                       of its d(dir) row is 0, a written row's is 1)
 //   dx1[n] = -sum_k d(dir_k)
 //   dW1, db1, dWpos, dbpos             (per-workgroup partial slabs in registers -> summed in a
 //                                       fixed order by a second kernel)
@@ -456,14 +459,27 @@ void cost_volume_bwd_kernel(
   // it uses into that branch, next to the store, and wait for them there.
   float gqn[OT];
   int amn[OT], rkm = -1;
+  // the query's live rows (ranked mode): bit r is set iff some output's argmax is row r, g' = 0
+  // included.  Every other row's dz0 and d(dir) are exactly +0 (dh0 starts at +0 and adds only
+  // +-0 products; dz0 = dh0 * slope; d(dir) is an fma chain over +0 from +0), and the row sum
+  // adds them to an accumulator that is never -0, so such a row is not written: its slot gets
+  // an out-of-range offset, as rows >= k, and its d(dir) row carries .w = 0 (live: 1), by
+  // which cv_rows_sum_lds_kernel skips it.  Wave-uniform (the lanes' argmax values OR-ed
+  // through DPP into a scalar, no LDS); with D_IN = 64 both channel-half waves hold the same
+  // argmax table and so the same mask.  Plain mode writes every row.
+  unsigned livem = 0u;
   auto tables = [&](int m, int u) {
+    unsigned lv = 0u;
 #pragma unroll
     for (int t = 0; t < OT; ++t) {
       gqn[t] = dvq[t] * (ovq[t] > 0.f ? 1.f : kSlope);
       amn[t] = amq[t];
+      lv |= 1u << (amn[t] & 31);
     }
+    livem = wave_or_u32(lv);
     rkm = rkn;
-    const int slot = lane < k ? (ranked ? rkm : (nbase + m) * k + lane) : -1;
+    const bool keep = !ranked || ((livem >> (lane & 31)) & 1u);
+    const int slot = lane < k && keep ? (ranked ? rkm : (nbase + m) * k + lane) : -1;
     float* x = dX(u);
     x[lane] = xv0 - qs0;
     x[2 * kRows + lane] = xv1 - qs1;
@@ -517,6 +533,7 @@ void cost_volume_bwd_kernel(
     const bool act = CS == 1 || n < q1;  // wave-uniform
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;  // d(dir) of the lane's row (direction pass)
     const int rkv = rkm;                 // this query's row slots (dirs store)
+    const unsigned lvv = livem;          // and its live rows
     float gq[OT];
     int amc[OT];
 #pragma unroll
@@ -713,7 +730,8 @@ void cost_volume_bwd_kernel(
       const bool row = lane < k;  // lanes >= 32 never (k <= 32)
       if (ranked) {
         const unsigned off = (row && rkv >= 0) ? (unsigned)rkv * 16u : kOOB;
-        __builtin_amdgcn_raw_buffer_store_b128(f32x4{g0, g1, g2, 0.f}, dirr, (int)off, 0, 0);
+        const float fl = (lvv >> (lane & 31)) & 1u ? 1.f : 0.f;  // was its dP2 row written
+        __builtin_amdgcn_raw_buffer_store_b128(f32x4{g0, g1, g2, fl}, dirr, (int)off, 0, 0);
       } else {
         const unsigned off = row ? ((unsigned)((nbase + n) * k + lane)) * 12u : kOOB;
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g0), dirr, (int)off, 0, 0);
@@ -874,12 +892,32 @@ __device__ __forceinline__ float4 vadd(float4 a, float4 b) {
 }
 // The sums stream the rows through LDS: a workgroup owns KB consecutive keys,
 // whose segments are one contiguous run of rows; windows of WR rows are read with
-// contiguous float4 loads (the whole workgroup, 16 per thread, the next window in flight
-// while this one is summed) into LDS, then every (key, chunk) thread adds the rows of its
-// segment inside the window in ascending
-// order (round 4; the round-3 kernel, one thread per (key, chunk) reading rows straight from
-// memory, read each row as 144-byte pieces of ~7 segments per load instruction and waited on
-// its longest segment per wave: ~2.6 TB/s at cross0).
+// contiguous float4 loads (the whole workgroup, the next window in flight while this one is
+// summed) into LDS, then every (key, chunk) thread adds the rows of its segment inside the
+// window in ascending order (round 4; the round-3 kernel, one thread per (key, chunk) reading
+// rows straight from memory, read each row as 144-byte pieces of ~7 segments per load
+// instruction and waited on its longest segment per wave: ~2.6 TB/s at cross0).
+//
+// Dead rows: the backward leaves the dP2 row of a neighbour no output routes to unwritten and
+// marks it in the .w of its d(dir) float4 (1 live, 0 dead; cost_volume_bwd_kernel).  Such a
+// row is exactly +0 and the accumulator is never -0 (it starts at +0, and a sum is -0 only if
+// both operands are), so leaving it out of the sum changes no bit: its LDS rows are set to
+// zero and its memory -- stale workspace, possibly NaN -- is never loaded.  The summation
+// loop and its order are as before.  The flags of the rows a thread loads are read one window
+// further ahead than the rows (4-byte loads of .w), so the rows of the next window still go
+// out right after the barrier and land under this window's sums; only the first window of a
+// workgroup pays a flag round trip before its rows.  Measured with tools/bench_cv_bwd.py at
+// cross0 (16 x 8192 x 32 rows, D = 32; 57 % of its rows are live, against 29-31 % in the
+// train step of bench.py; rocprofv3 kernel trace, us per launch):
+//   every row read (before)                                   158
+//   flags, rows loaded under `if (flag)`, 64 KiB window       188  (a wait per load)
+//   flags, branch-free buffer loads, 64 KiB window            123
+//   the same, 32 KiB window (4 workgroups per CU, not 2)       93  <- this kernel
+//   the same, 16 KiB window                                    95
+//   32 KiB, no flags ahead: a window's d(dir) rows first, its
+//   rows after the barrier by the flags then in LDS             97  (no load under the sums)
+// With fewer bytes the kernel is bound by load latency, not bandwidth, hence the smaller
+// window; D = 64 / 128 / 256 there (82 / 96 / 99 % live): 62 -> 45, 31 -> 26, 31 -> 26 us.
 template <int D>
 __global__ __launch_bounds__(256) void cv_rows_sum_lds_kernel(long long nkeys,
                                                               const float* __restrict__ rows,
@@ -889,43 +927,83 @@ __global__ __launch_bounds__(256) void cv_rows_sum_lds_kernel(long long nkeys,
                                                               float* __restrict__ dx2) {
   constexpr int CH = D / 4 + 1;
   constexpr int KB = 256 / CH;          // keys per workgroup
-  constexpr int WR = 4096 / CH;         // rows per LDS window (64 KiB; 32 KiB measured the same)
+  constexpr int WF4 = 2048;             // float4 elements of the LDS window (32 KiB)
+  constexpr int WR = WF4 / CH;          // rows per LDS window
   __shared__ float4 win[WR * CH];
   constexpr int DQ = D / 4;
-  const float4* src = reinterpret_cast<const float4*>(rows);
-  const float4* srd = reinterpret_cast<const float4*>(dirs);
   const long long k0 = (long long)blockIdx.x * KB;
   const int t = threadIdx.x;
   const int kl = t / CH, ch = t - (t / CH) * CH;
   const long long key = k0 + kl;
   const bool mine = kl < KB && key < nkeys;
   const long long kend = std::min<long long>(k0 + KB, nkeys);
-  const int s0 = offsets[k0], s1 = offsets[kend];
+  // uniform over the workgroup: the windows' buffer resources are built from them
+  const int s0 = __builtin_amdgcn_readfirstlane(offsets[k0]);
+  const int s1 = __builtin_amdgcn_readfirstlane(offsets[kend]);
   const int j0 = mine ? offsets[key] : 0, j1 = mine ? offsets[key + 1] : 0;
-  constexpr int NPT = (WR * CH + 255) / 256;  // float4 loads per thread and window
+  constexpr int NPT = (WR * DQ + 255) / 256;  // dP2 float4 loads per thread and window
+  constexpr int NDT = (WR + 255) / 256;       // d(dir) float4 loads
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 nx[NPT];  // the next window, in flight while the current one is summed
-  // window element i < nr*DQ: dP2 chunk i % DQ of row i / DQ; then the nr d(dir) rows
-  auto fetch = [&](int w) {
-    const int nr = min(WR, s1 - w);
+  float4 nx[NPT], nd[NDT];  // the next window, in flight while the current one is summed
+  float fl[NPT];            // the flags of the rows this thread loads, one window further ahead
+  // Every load goes through a buffer resource over its window (uniform base, < 64 KiB): an
+  // out-of-range offset reads exact zeros without a branch, so a window's loads are all in
+  // flight together, and a window past the segment's end (the unconditional prefetch of the
+  // last iterations: a branch around it made the compiler wait for every load before the
+  // sums) is an empty resource
+  auto ld4 = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                       __uint_as_float(v[3]));
+  };
+  // the live flags of window w: .w of the d(dir) row of the row that load q of fetch(w) reads
+  auto flags = [&](int w) {
+    const int nr = min(WR, s1 - min(w, s1));  // none past the end
+    const __amdgpu_buffer_rsrc_t dr = rsrc_of(dirs + (long long)w * 4, (long long)nr * 16);
 #pragma unroll
     for (int q = 0; q < NPT; ++q) {
       const int i = t + 256 * q;
-      nx[q] = i < nr * DQ ? src[(long long)w * DQ + i]
-                          : (i < nr * CH ? srd[w + (i - nr * DQ)] : make_float4(0.f, 0.f, 0.f, 0.f));
+      fl[q] = bload(dr, i < nr * DQ ? (unsigned)(i / DQ) * 16u + 12u : kOOB);
     }
   };
-  if (s0 < s1) fetch(s0);
+  // window w (fl = its flags): element i < nr*DQ is dP2 chunk i % DQ of row i / DQ, loaded only
+  // where the row is live -- a dead slot is stale workspace, never read -- and exact zeros
+  // elsewhere; then the nr d(dir) rows, all of them written by the backward
+  auto fetch = [&](int w) {
+    const int nr = min(WR, s1 - min(w, s1));  // none past the end
+    const __amdgpu_buffer_rsrc_t rr = rsrc_of(rows + (long long)w * D, (long long)nr * D * 4);
+    const __amdgpu_buffer_rsrc_t dr = rsrc_of(dirs + (long long)w * 4, (long long)nr * 16);
+#pragma unroll
+    for (int q = 0; q < NPT; ++q) {
+      const int i = t + 256 * q;
+      nx[q] = ld4(rr, i < nr * DQ && fl[q] != 0.f ? (unsigned)i * 16u : kOOB);
+    }
+#pragma unroll
+    for (int q = 0; q < NDT; ++q) {
+      const int i = t + 256 * q;
+      nd[q] = ld4(dr, i < nr ? (unsigned)i * 16u : kOOB);
+    }
+  };
+  if (s0 < s1) {
+    flags(s0);
+    fetch(s0);
+    flags(s0 + WR);
+  }
   for (int w = s0; w < s1; w += WR) {
     const int nr = min(WR, s1 - w);
 #pragma unroll
     for (int q = 0; q < NPT; ++q) {
       const int i = t + 256 * q;
-      if (i < nr * CH)
-        win[i < nr * DQ ? (i / DQ) * CH + i % DQ : (i - nr * DQ) * CH + DQ] = nx[q];
+      if (i < nr * DQ) win[(i / DQ) * CH + i % DQ] = nx[q];
+    }
+#pragma unroll
+    for (int q = 0; q < NDT; ++q) {
+      const int i = t + 256 * q;
+      if (i < nr) win[i * CH + DQ] = nd[q];
     }
     __syncthreads();
-    if (w + WR < s1) fetch(w + WR);
+    fetch(w + WR);
+    flags(w + 2 * WR);
     const int a = max(j0, w) - w, b = min(j1, w + nr) - w;
     int j = a;
     for (; j + 8 <= b; j += 8) {  // eight rows' LDS reads in flight, adds in row order

@@ -14,6 +14,10 @@
 //                        partials (fixed assignment, summed by colsum: no float atomics)
 // LeakyReLU' is read from the sign of the activation output (slope 0.1 > 0: h > 0 <=> z > 0,
 // and z = 0 takes the slope as torch's leaky_relu_backward does).
+// The fused backward (cvw_fused_bwd_kernel) in ranked mode follows the contract of
+// cv_rows_sum_lds_kernel (cost_volume.hip): the dP2 row of a neighbour no output's argmax
+// points at is exactly +0 and is not written; the .w of its d(dir) float4 says so (1 = row
+// written, 0 = not).  Plain mode writes every row.
 #include <algorithm>
 
 #include "kdpc_common.h"
@@ -492,6 +496,11 @@ __global__ __launch_bounds__(2 * D) __attribute__((amdgpu_waves_per_eu(D == 128 
   // dh0 = M W1 (M[r][o] = g'[o] [am[o] == r]) is 8 outputs' planes masked per 16-bit half
   __shared__ __attribute__((aligned(16))) __bf16 gpl[2][3][D];
   __shared__ __attribute__((aligned(16))) unsigned short gam16[2][D];
+  // ranked rows: the query's live rows, bit r set iff some output's argmax (gam[p][.].y) is row
+  // r, as one partial mask per staging wave.  A row no output routes to has dz0 = d(dir) = +0
+  // exactly: its dP2 row is not written and its d(dir) row carries .w = 0 (live: 1), the flag
+  // by which cv_rows_sum_lds_kernel skips it (cost_volume.hip)
+  __shared__ unsigned livew[2][D / 64];
   __shared__ __attribute__((aligned(16))) float4 red[G::RG][G::C4];  // dP1 partials
   __shared__ __attribute__((aligned(16))) float4 red2[NG2][32];      // d(dir) partials
   __shared__ __attribute__((aligned(16))) float4 wposT[D];           // Wpos rows (x, y, z, 0)
@@ -563,6 +572,8 @@ __global__ __launch_bounds__(2 * D) __attribute__((amdgpu_waves_per_eu(D == 128 
       gpl[p][1][t] = gm;
       gpl[p][2][t] = gl;
       gam16[p][t] = (unsigned short)av;
+      const unsigned lv = wave_or_u32(1u << (av & 31u));  // t < D: whole waves
+      if (lane == 0) livew[p][w] = lv;
     }
   };
 
@@ -590,6 +601,7 @@ __global__ __launch_bounds__(2 * D) __attribute__((amdgpu_waves_per_eu(D == 128 
     if constexpr (W::PREFETCH) next_loads();  // in flight under this query's MFMAs
     float* H = Hs[p];
     const float2* ga = gam[p];
+    unsigned live = 0u;  // this query's live rows (read in the column pass)
     // ---- dh0 = M W1 (rows = neighbours, columns 32w .. +31 of Din) on mfma_x6: K-step ks,
     // lane half h: outputs o = 16 ks + 8 h + j; A[l32][o] = planes of g'[o] where am[o] == l32
     // (a 16-bit mask per output from the packed u16 rows: (am ^ l32) - 1 < 0 <=> am == l32)
@@ -668,13 +680,19 @@ __global__ __launch_bounds__(2 * D) __attribute__((amdgpu_waves_per_eu(D == 128 
     {
       float4 sp = make_float4(0.f, 0.f, 0.f, 0.f);
       float* d2 = dp2_rows + (long long)q * k * D + 4 * c4;
+      if (ranked) {
+        live = livew[p][0];
+#pragma unroll
+        for (int i = 1; i < D / 64; ++i) live |= livew[p][i];
+      }
 #pragma unroll
       for (int i = 0; i < G::RPT; ++i) {
         const int r = rg + G::RG * i;
         const float4 v = *reinterpret_cast<const float4*>(H + r * G::LD + 4 * c4);
         const float4 dr = dirs[p][r];
         if (ranked) {
-          if (r < k && rk[i] >= 0) *reinterpret_cast<float4*>(rows + (long long)rk[i] * D + 4 * c4) = v;
+          if (r < k && rk[i] >= 0 && ((live >> r) & 1u))
+            *reinterpret_cast<float4*>(rows + (long long)rk[i] * D + 4 * c4) = v;
         } else if (r < k && dp2_rows) {  // null: the pull-form caller sums per point itself
           *reinterpret_cast<float4*>(d2 + (long long)r * D) = v;
         }
@@ -750,7 +768,7 @@ __global__ __launch_bounds__(2 * D) __attribute__((amdgpu_waves_per_eu(D == 128 
       if (row && ranked) {
         if (rkd >= 0)
           *reinterpret_cast<float4*>(rows + (long long)b * n1 * k * D + (long long)rkd * 4) =
-              make_float4(v.x, v.y, v.z, 0.f);
+              make_float4(v.x, v.y, v.z, (live >> l32) & 1u ? 1.f : 0.f);
       } else if (row && ddir_rows) {
         float* dd = ddir_rows + ((long long)q * k + l32) * 3;
         dd[0] = v.x;

@@ -74,6 +74,24 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
   return v;
 }
 
+// Bitwise OR over the wave's 64 lanes as a wave-uniform value (a scalar register): pair,
+// quad, 8- and 16-lane steps through DPP (VALU operand modifiers, no LDS; after them every
+// lane of a 16-lane row holds its row's OR), then the four rows through readlanes.  Every lane
+// must be active.
+template <int CTRL>
+__device__ __forceinline__ unsigned or_dpp(unsigned v) {
+  return v | (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+__device__ __forceinline__ unsigned wave_or_u32(unsigned v) {
+  v = or_dpp<0xB1>(v);   // quad_perm [1,0,3,2]: pairs
+  v = or_dpp<0x4E>(v);   // quad_perm [2,3,0,1]: quads
+  v = or_dpp<0x141>(v);  // row_half_mirror: 8 lanes
+  v = or_dpp<0x140>(v);  // row_mirror: 16 lanes
+  const int s = (int)v;
+  return (unsigned)(__builtin_amdgcn_readlane(s, 0) | __builtin_amdgcn_readlane(s, 16) |
+                    __builtin_amdgcn_readlane(s, 32) | __builtin_amdgcn_readlane(s, 48));
+}
+
 // lane l receives lane l-1's value; lane 0 receives `fill` (DPP wave_shr:1, gfx9).
 __device__ __forceinline__ float wave_shr1(float v, float fill) {
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v),

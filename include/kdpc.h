@@ -507,6 +507,30 @@ int kdpc_flow_propagate(int b, int n, int c, long long m_total, int max_len,
                         const float *anchors, const float *vals, const float *qry,
                         const long long *offsets, float *out, int *idx_out, void *stream);
 
+/* ---- Chamfer distance (self-supervised training, selfsup.py; no reference counterpart:
+ *      PointPWC-Net's loss takes it from a dense (B,N,M) distance matrix) ----------------- */
+
+/* Nearest neighbour in both directions in one launch.  a (B,N,3), bp (B,M,3) ->
+ * dist_ab (B,N) = min_j dist(a_i, bp_j) squared, idx_ab (B,N) int32 in [0,M) the lowest j that
+ * attains it; dist_ba (B,M), idx_ba (B,M) in [0,N) with the roles swapped.  Distances are the
+ * direct-difference form and the comparison is strict < in ascending index: the first column
+ * of kdpc_three_nn, bit for bit (and defined for N, M < 3).  A NaN distance never wins (a row
+ * with a NaN coordinate gets dist +inf, idx 0).  Writes its four outputs only: no workspace,
+ * no atomics, capture-safe.  N, M >= 1, B <= 65535, B * max(N,M) < 2^31; B == 0 is a no-op. */
+int kdpc_chamfer_fwd(int b, int n, int m, const float *a, const float *bp, float *dist_ab,
+                     int *idx_ab, float *dist_ba, int *idx_ba, void *stream);
+
+/* Gradient with respect to a of sum_i g_ab[i] dist_ab[i] + sum_j g_ba[j] dist_ba[j], the
+ * neighbour choices held fixed:
+ *   da[i] = 2 g_ab[i] (a_i - bp[idx_ab[i]]) + sum_{j : idx_ba[j] = i} 2 g_ba[j] (a_i - bp_j)
+ * idx_ab, g_ab (B,N); g_ba (B,M); offsets_ba (B*N+1), perm_ba (B*M): kdpc_csr_build of idx_ba
+ * with key space N.  da (B,N,3) is overwritten; the direct term first, then the CSR run in
+ * order (deterministic).  g_ba, offsets_ba and perm_ba may be NULL together (one direction
+ * only); bp's gradient is this entry with the roles swapped.  Sizes as kdpc_chamfer_fwd. */
+int kdpc_chamfer_bwd(int b, int n, int m, const float *a, const float *bp, const int *idx_ab,
+                     const float *g_ab, const int *offsets_ba, const int *perm_ba,
+                     const float *g_ba, float *da, void *stream);
+
 /* ---- skinny 1x1-layer weight gradients (dense_small.hip) ---------------------------- */
 
 /* out (O x I) = A^T B for row-major A (R x O), B (R x I), min(O,I) <= 4, O + I <= 512: slab

@@ -24,6 +24,7 @@ import torch.distributed as dist
 
 import kdpc_native as _nat
 import loss_functions
+import selfsup
 import wgrad
 
 
@@ -238,6 +239,33 @@ class FlowTrainStep:
         kw = {} if fps is None else {"fps_idx": fps}
         flows, fps1, _, _, _, _, _, _ = self.model(pos1, pos2, color1, color2, **kw)
         loss = self.loss_fn(flows, flow, fps1)
+        loss.backward()
+        self.opt.step()
+        self.opt.zero_grad(set_to_none=True)
+        return loss.detach()
+
+
+class SelfSupTrainStep:
+    """FlowTrainStep without ground truth: fwd -> selfsup.multiScaleChamferSmooth(flows, pc1,
+    pc2) -> bwd -> optimizer step, for raw scans that carry no flow labels."""
+
+    def __init__(self, model, optimizer, loss_fn=None):
+        self.model = model
+        self.opt = optimizer
+        self.loss_fn = loss_fn or selfsup.multiScaleChamferSmooth
+        self.prefetch = FpsPrefetch()
+
+    def __call__(self, pos1, pos2, color1=None, color2=None, next_batch=None):
+        """next_batch: optional (pos1, pos2, ...) of the following step (FpsPrefetch)."""
+        color1 = pos1 if color1 is None else color1
+        color2 = pos2 if color2 is None else color2
+        fps = self.prefetch.take(pos1, pos2)
+        if next_batch is not None:
+            self.prefetch.launch(self.model, next_batch[0], next_batch[1])
+        self.model.train()
+        kw = {} if fps is None else {"fps_idx": fps}
+        flows, _, _, pc1, pc2, _, _, _ = self.model(pos1, pos2, color1, color2, **kw)
+        loss = self.loss_fn(flows, pc1, pc2)
         loss.backward()
         self.opt.step()
         self.opt.zero_grad(set_to_none=True)
@@ -751,6 +779,22 @@ def graphed_flow_step(model, optimizer, example_inputs, loss_fn=None, warmup=3, 
         return loss_fn(flows, flow, fps1)
     return GraphedStep(run, model.parameters(), optimizer, example_inputs, warmup,
                        prefetch_fn=_plan_fn(model) if prefetch else None, overlap=overlap)
+
+
+def graphed_selfsup_step(model, optimizer, example_inputs, loss_fn=None, warmup=3, prefetch=True,
+                         overlap=None):
+    """SelfSupTrainStep as a GraphedStep; example_inputs = (pos1, pos2), built like
+    graphed_flow_step (the loss's searches and CSRs are captured with the rest of the step)."""
+    loss_fn = loss_fn or selfsup.multiScaleChamferSmooth
+    model.train()
+
+    def run(pos1, pos2, fps=None):
+        kw = {} if fps is None else {"fps_idx": fps}
+        flows, _, _, pc1, pc2, _, _, _ = model(pos1, pos2, pos1, pos2, **kw)
+        return loss_fn(flows, pc1, pc2)
+    return GraphedStep(run, model.parameters(), optimizer, example_inputs, warmup,
+                       prefetch_fn=_plan_fn(model) if prefetch else None, n_prefetch=2,
+                       overlap=overlap)
 
 
 def graphed_kd_step(teacher, student, optimizer, example_inputs, gamma=0.3, beta=0.8, layer=3,

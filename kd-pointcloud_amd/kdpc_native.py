@@ -4,7 +4,8 @@ Two layers over libkdpc_hip.so (the C ABI in include/kdpc.h):
   * torch.ops.kdpc (lib/libkdpc_torch.so, torch_ops/kdpc_torch_ops.cpp): every C entry
     point registered as a torch operator with a schema, TORCH_CHECKed inputs, outputs and
     scratch from the caching allocator, launched on the current torch stream.  Every op
-    function below goes through it;
+    function below goes through it (the Chamfer operators of the self-supervised loss are
+    registered by the same library as torch.ops.kdpc_selfsup);
   * a ctypes binding of the bare C ABI (load_library, _SIGNATURES), used by the C-ABI
     tests (export / arity / argument validation), by build-id verification and by the two
     ops that have no torch operator (knn_point_evals, flow_propagate).
@@ -106,6 +107,8 @@ _SIGNATURES = {
     "kdpc_idw_blend_bwd_vals": [_c_int] * 4 + [_vp] * 5 + [_c_int, _vp],
     "kdpc_idw_blend_bwd_coords": [_c_int] * 4 + [_vp] * 7 + [_c_int, _vp],
     "kdpc_flow_propagate": [_c_int] * 3 + [_c_longlong, _c_int] + [_vp] * 7,
+    "kdpc_chamfer_fwd": [_c_int] * 3 + [_vp] * 7,
+    "kdpc_chamfer_bwd": [_c_int] * 3 + [_vp] * 9,
     "kdpc_dense_tn_small_workspace_bytes": [_c_int] * 3,
     "kdpc_dense_tn_small": [_c_int] * 3 + [_vp] * 4 + [_c_size, _vp],
     "kdpc_dense_small": [_c_int] * 3 + [_vp] * 5,
@@ -261,10 +264,12 @@ def _gpu(t, name):
     return t
 
 
-def _op(entry, op, *args, work=None):
-    """Run torch.ops.kdpc.<op>; `entry` is the C entry point it launches (the unit the
-    bench's live roofline brackets), `work` = (algorithmic bytes, flops) of the launch."""
-    fn = getattr(_ops or load_ops(), op)
+def _op(entry, op, *args, work=None, ns=None):
+    """Run torch.ops.kdpc.<op> (torch.ops.<ns>.<op> of the same library when ns is given);
+    `entry` is the C entry point it launches (the unit the bench's live roofline brackets),
+    `work` = (algorithmic bytes, flops) of the launch."""
+    ops = _ops or load_ops()
+    fn = getattr(ops if ns is None else getattr(torch.ops, ns), op)
     t = _timer
     if t is not None and entry in t.names:
         e0 = torch.cuda.Event(enable_timing=True)
@@ -844,6 +849,33 @@ def flow_propagate(anchors, vals, qry, offsets, max_len, return_idx=False):
           idx.data_ptr() if return_idx else None, _stream(anchors),
           work=(12.0 * M + 4.0 * C * M + (12 + 4 * C) * B * N, 8.0 * M * N))
     return (out, idx) if return_idx else out
+
+
+# ------------------------------------------------------------------ Chamfer distance
+def chamfer_fwd(a, b):
+    """a (B,N,3), b (B,M,3) -> (dist_ab (B,N), idx_ab (B,N) i32, dist_ba (B,M), idx_ba (B,M)
+    i32): each point's squared distance to, and the index of, its nearest point of the other
+    cloud (three_nn's first column, both directions in one launch).  See include/kdpc.h."""
+    B, N, _ = _gpu(a, "a").shape
+    M = _gpu(b, "b").shape[1]
+    return _op("kdpc_chamfer_fwd", "chamfer_fwd", a, b, ns="kdpc_selfsup",
+               work=(B * (12 * (N + M) + 8 * (N + M)), 2.0 * 8 * B * N * M))
+
+
+def chamfer_bwd(a, b, idx_ab, g_ab, csr_ba=None, g_ba=None):
+    """-> da (B,N,3), the gradient of sum g_ab dist_ab + sum g_ba dist_ba with respect to a.
+    csr_ba: csr_of(idx_ba, N) with g_ba (B,M), or both None (the a -> b direction alone).  b's
+    gradient: chamfer_bwd(b, a, idx_ba, g_ba, csr_of(idx_ab, M), g_ab)."""
+    B, N, _ = _gpu(a, "a").shape
+    M = _gpu(b, "b").shape[1]
+    if (csr_ba is None) != (g_ba is None):
+        raise ValueError("chamfer_bwd: csr_ba and g_ba are given together or not at all")
+    two = csr_ba is not None
+    return _op("kdpc_chamfer_bwd", "chamfer_bwd", a, b, idx_ab, g_ab,
+               csr_ba.offsets if two else None, csr_ba.perm if two else None, g_ba,
+               ns="kdpc_selfsup",
+               work=(B * (12 * N + 12 * N + 8 * N + 12 * N + (20 * M + 4 * N if two else 0)),
+                     9.0 * B * (N + (M if two else 0))))
 
 
 # ------------------------------------------------------------------- fused WeightNet

@@ -1036,6 +1036,66 @@ void dense_small_out(Tensor x, Tensor m, c10::optional<Tensor> bias, Tensor y) {
   check(kdpc_dense_small(r, k, n, F(x), F(m), bp, F(y), stream_of(x)), "dense_small");
 }
 
+// ------------------------------------------------- Chamfer distance (csrc/chamfer.hip)
+void chamfer_clouds(const Tensor& a, const Tensor& b, const char* op) {
+  dev(a, kF, "a"), dev(b, kF, "b"), same_device(a, b, "b");
+  TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && a.size(0) == b.size(0) && a.size(2) == 3 &&
+                  b.size(2) == 3 && a.size(1) >= 1 && b.size(1) >= 1,
+              "kdpc: ", op, " expects a (B,N,3), b (B,M,3) with N, M >= 1");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> chamfer_fwd(Tensor a, Tensor b) {
+  chamfer_clouds(a, b, "chamfer_fwd");
+  GUARD(a);
+  const int64_t bs = a.size(0), n = a.size(1), m = b.size(1);
+  Tensor dist_ab = empty_f({bs, n}, a), dist_ba = empty_f({bs, m}, a);
+  Tensor idx_ab = empty_i({bs, n}, a), idx_ba = empty_i({bs, m}, a);
+  check(kdpc_chamfer_fwd(bs, n, m, F(a), F(b), F(dist_ab), I(idx_ab), F(dist_ba), I(idx_ba),
+                         stream_of(a)), "chamfer_fwd");
+  return {dist_ab, idx_ab, dist_ba, idx_ba};
+}
+
+Tensor chamfer_bwd(Tensor a, Tensor b, Tensor idx_ab, Tensor g_ab,
+                   c10::optional<Tensor> offsets_ba, c10::optional<Tensor> perm_ba,
+                   c10::optional<Tensor> g_ba) {
+  chamfer_clouds(a, b, "chamfer_bwd");
+  dev(idx_ab, kI, "idx_ab"), dev(g_ab, kF, "g_ab");
+  same_device(a, idx_ab, "idx_ab"), same_device(a, g_ab, "g_ab");
+  const int64_t bs = a.size(0), n = a.size(1), m = b.size(1);
+  TORCH_CHECK(idx_ab.numel() == bs * n && g_ab.numel() == bs * n,
+              "kdpc: chamfer_bwd: idx_ab and g_ab must be (B,N)");
+  const bool two = g_ba.has_value();
+  TORCH_CHECK(offsets_ba.has_value() == two && perm_ba.has_value() == two,
+              "kdpc: chamfer_bwd: offsets_ba, perm_ba and g_ba are given together or not at all");
+  if (two) {
+    dev(*offsets_ba, kI, "offsets_ba"), dev(*perm_ba, kI, "perm_ba"), dev(*g_ba, kF, "g_ba");
+    same_device(a, *offsets_ba, "offsets_ba"), same_device(a, *perm_ba, "perm_ba");
+    same_device(a, *g_ba, "g_ba");
+    TORCH_CHECK(offsets_ba->numel() == bs * n + 1 && perm_ba->numel() == bs * m &&
+                    g_ba->numel() == bs * m,
+                "kdpc: chamfer_bwd: offsets_ba (B*N+1), perm_ba (B*M), g_ba (B,M) expected");
+  }
+  GUARD(a);
+  Tensor da = empty_f({bs, n, 3}, a);
+  check(kdpc_chamfer_bwd(bs, n, m, F(a), F(b), I(idx_ab), F(g_ab),
+                         two ? I(*offsets_ba) : nullptr, two ? I(*perm_ba) : nullptr,
+                         two ? F(*g_ba) : nullptr, F(da), stream_of(a)), "chamfer_bwd");
+  return da;
+}
+
+// The self-supervised loss's operators, in a namespace of their own (torch.ops.kdpc_selfsup):
+// torch.ops.kdpc stays the surface of the supervised model's layers.
+TORCH_LIBRARY(kdpc_selfsup, m) {
+  m.def("chamfer_fwd(Tensor a, Tensor b) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("chamfer_bwd(Tensor a, Tensor b, Tensor idx_ab, Tensor g_ab, Tensor? offsets_ba, "
+        "Tensor? perm_ba, Tensor? g_ba) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(kdpc_selfsup, CUDA, m) {
+  m.impl("chamfer_fwd", chamfer_fwd);
+  m.impl("chamfer_bwd", chamfer_bwd);
+}
+
 TORCH_LIBRARY(kdpc, m) {
   // reference pointnet2_cuda surface (pointnet2_api.cpp:10-24), in-place, returns 1
   m.def("ball_query_wrapper(int b, int n, int m, float radius, int nsample, Tensor new_xyz, "
